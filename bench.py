@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: p50 dashboard refresh + rows rendered on a synthetic MI355X cluster.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it starts the
+cluster, runs W warm-up and K timed refreshes of the flagship schedule, and
+prints the result line. ``--full`` adds every secondary figure described
+below (the reference schedule's replay as the measured baseline, cold opens,
+the all-pages composite, route switches, detail pages, the React mounts).
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as ``DIR/table_rows.npy``: the rows each of the five pages rendered (float64,
+in sidebar order). The synthetic cluster is seeded, so two builds run with the
+same arguments can be compared row count for row count.
 
 BASELINE.json metric: "p50 dashboard refresh (ms) + GPU nodes/pods rendered at
 1/2/4/8-node cluster". One rank per GPU; rank r plays node r of an N-node
@@ -19,8 +29,8 @@ cluster of 8×MI355X nodes (weak scaling: per-node work is fixed as N grows).
   ServiceMonitor) into the TSDB, HIP device r → GPU 0 of node r, so GPU 0 of
   every node reports real power / HBM / activity;
 * rank 0 drives the SHIPPED plugin data layer (src/, Node.js) over real HTTP:
-  the reference plugin's request schedule is replayed first as the measured
-  baseline (untimed), then the flagship schedule runs W warm-up refreshes and
+  with ``--full`` the reference plugin's request schedule is replayed first as the
+  measured baseline (untimed); the flagship schedule runs W warm-up refreshes and
   EXACTLY K timed refreshes bracketed by barrier + torch.cuda.synchronize()
   on every rank; ms_per_step is the MAX over ranks.
 
@@ -33,10 +43,10 @@ next to the reference's). The reference's buttons run different chains per
 page — the provider's 4 serial requests on the first four, the Metrics page's
 probe + 4 queries on the last — and each is replayed as wired.
 
-The "all pages" composite (every page's data + all views rebuilt in one go,
-which no single reference button does) is reported as a secondary figure.
-Render in the timed click = view-model → HTML string (the IR renderer's
-output). Untimed, every page is also mounted and re-rendered through the
+With ``--full``, the "all pages" composite (every page's data + all views rebuilt
+in one go, which no single reference button does) is reported as a secondary
+figure. Render in the timed click = view-model → HTML string (the IR renderer's
+output). Untimed, with ``--full`` every page is also mounted and re-rendered through the
 shipped React renderer, on the harness React and on real React 18.3.1
 production builds (``render_per_page`` / ``render_per_page_react_dom``).
 Data is synthetic (no cluster, no network); say so in the JSON.
@@ -76,7 +86,24 @@ def parse_args(argv=None):
     p.add_argument("--out", default=None, help="also write the full result JSON here")
     p.add_argument("--order", default="reference-first", choices=["reference-first", "amd-first"],
                    help="which schedule's phases run first (the figures must not depend on it)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure every secondary figure: the reference schedule's replay (baseline), cold opens, "
+                        "the all-pages composite, route switches, detail pages, React mounts")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (rows rendered per page) as DIR/table_rows.npy")
     return p.parse_args(argv)
+
+
+PAGES = ("overview", "devicePlugins", "nodes", "pods", "metrics")  # sidebar order (bench/pageRender.js)
+
+
+def dump_outputs(directory, amd_pages):
+    """DIR/table_rows.npy: the row count each page's last timed click returned, float64, in PAGES order."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    rows = np.array([amd_pages[pg]["tableRows"] for pg in PAGES], dtype=np.float64)
+    np.save(os.path.join(directory, "table_rows.npy"), rows)
 
 
 def _p50(xs):
@@ -160,7 +187,7 @@ def main(argv=None) -> int:
         # The reference schedule runs in a Node process of its own: neither
         # schedule's figures depend on the heap and JIT state the other left
         # (the 1,000-node composite moved by 18% with the order otherwise).
-        ref_drv = Driver(server.url)
+        ref_drv = Driver(server.url) if args.full else None
 
         def call(*a, driver=None, **k):
             """drv.call + a progress line on stderr (a long 1,000-node run stays visibly alive)."""
@@ -188,12 +215,38 @@ def main(argv=None) -> int:
                 ref_drv.close()
                 return out
 
-            if args.order == "reference-first":
-                R = reference_phases()
+            def full_phases():
+                """--full: every secondary figure of the flagship schedule, and the reference's replay (all untimed)."""
+                # Untimed: every page mounted in the harness React and re-rendered
+                # after a refresh (element count, mount / re-render ms); and on real
+                # React 18.3.1 (production builds) when they are vendored.
+                from headlamp_intel_gpu_plugin_amd.utils.reactumd import PROD_BUILDS, umd_dir
+                react_out = call("pages", "amd", n=1, react=True, reactUmdDir=umd_dir(PROD_BUILDS))
+                amd_react = react_out.get("react") or {}
+                amd_react_dom = react_out.get("reactDom") or {}
+                # Secondary: the all-pages composite refresh.
+                drv.call("steps", "amd", n=1)
+                amd = call("steps", "amd", n=max(3, args.steps // 2))
+                amd_switch = call("switch", "amd", n=5)
+                detail_out = call("detail", "amd", n=5)
+                detail = detail_out["detail"]
+                ref_out = reference_phases() if args.order == "amd-first" else R
+                ref_cold, ref_cold_pages, ref_pages, ref, ref_switch = (ref_out[k] for k in (
+                    "ref_cold", "ref_cold_pages", "ref_pages", "ref", "ref_switch"))
+                for r in (ref_pages, amd_pages, ref, amd, ref_cold_pages, amd_cold_pages):
+                    if r.get("error"):
+                        raise RuntimeError(r["error"])
+                return {"ref": ref, "ref_pages": ref_pages["pages"], "amd_pages": amd_pages["pages"], "ref_cold": ref_cold,
+                        "ref_switch": ref_switch, "amd": amd, "amd_cold": amd_cold, "amd_switch": amd_switch, "detail": detail,
+                        "ref_cold_pages": ref_cold_pages["pages"], "amd_cold_pages": amd_cold_pages["pages"],
+                        "detail_slow": detail_out.get("detailSlow"), "react": amd_react, "react_dom": amd_react_dom}
+
+            R = reference_phases() if args.full and args.order == "reference-first" else None
             # Flagship schedule.
-            call("cold", "amd", n=2)
-            amd_cold = call("cold", "amd", n=3)
-            amd_cold_pages = call("coldPages", "amd", n=5)
+            if args.full:
+                call("cold", "amd", n=2)
+                amd_cold = call("cold", "amd", n=3)
+                amd_cold_pages = call("coldPages", "amd", n=5)
             call("pages", "amd", n=max(1, args.warmup))
             D.barrier(info)
             quiet_sync()
@@ -202,36 +255,20 @@ def main(argv=None) -> int:
             quiet_sync()
             D.barrier(info)
             elapsed = time.perf_counter() - t0
-            # Untimed: every page mounted in the harness React and re-rendered
-            # after a refresh (element count, mount / re-render ms); and on real
-            # React 18.3.1 (production builds) when this image vendors them.
-            from headlamp_intel_gpu_plugin_amd.utils.reactumd import PROD_BUILDS, umd_dir
-            react_out = call("pages", "amd", n=1, react=True, reactUmdDir=umd_dir(PROD_BUILDS))
-            amd_react = react_out.get("react") or {}
-            amd_react_dom = react_out.get("reactDom") or {}
-            # Secondary: the all-pages composite refresh.
-            drv.call("steps", "amd", n=1)
-            amd = call("steps", "amd", n=max(3, args.steps // 2))
-            amd_switch = call("switch", "amd", n=5)
-            detail_out = call("detail", "amd", n=5)
-            detail = detail_out["detail"]
-            if args.order == "amd-first":
-                R = reference_phases()
-            ref_cold, ref_cold_pages, ref_pages, ref, ref_switch = (R[k] for k in (
-                "ref_cold", "ref_cold_pages", "ref_pages", "ref", "ref_switch"))
-            served = (server.stats() if args.control_plane == "process"
-                      else {"server_requests": fc.stats(), "scrapes": scraper.scrapes if scraper else 0})
-            for r in (ref_pages, amd_pages, ref, amd, ref_cold_pages, amd_cold_pages):
-                if r.get("error"):
-                    raise RuntimeError(r["error"])
-            result = {"ref": ref, "ref_pages": ref_pages["pages"], "amd_pages": amd_pages["pages"], "ref_cold": ref_cold, "ref_switch": ref_switch,
-                      "amd": amd, "amd_cold": amd_cold, "amd_switch": amd_switch, "detail": detail,
-                      "ref_cold_pages": ref_cold_pages["pages"], "amd_cold_pages": amd_cold_pages["pages"],
-                      "detail_slow": detail_out.get("detailSlow"), "react": amd_react, "react_dom": amd_react_dom,
-                      **served}
+            if amd_pages.get("error"):
+                raise RuntimeError(amd_pages["error"])
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, amd_pages["pages"])
+            if args.full:
+                result = full_phases()
+            else:
+                result = {"amd_pages": amd_pages["pages"]}
+            result.update(server.stats() if args.control_plane == "process"
+                          else {"server_requests": fc.stats(), "scrapes": scraper.scrapes if scraper else 0})
         finally:
             drv.close()
-            ref_drv.close()
+            if ref_drv:
+                ref_drv.close()
             server.stop()
             if scraper:
                 scraper.stop()
@@ -251,23 +288,21 @@ def main(argv=None) -> int:
         exporter.stop()
 
     if info.is_main:
-        amd_s = summarize(result["amd"]["latencies"])
-        ref_s = summarize(result["ref"]["latencies"])
-        rows = result["amd"]["rows"]
         pages = list(result["amd_pages"])
         per_page = {}
         for pg in pages:
             a = summarize(result["amd_pages"][pg]["latencies"])
-            r = summarize(result["ref_pages"][pg]["latencies"])
-            per_page[pg] = {"amd": round(a["p50"], 3), "reference": round(r["p50"], 3),
-                            "amd_p95": round(a["p95"], 3), "reference_p95": round(r["p95"], 3),
-                            "requests": {"amd": result["amd_pages"][pg]["requestsPerClick"],
-                                         "reference": result["ref_pages"][pg]["requestsPerClick"]},
-                            "speedup": round(r["p50"] / a["p50"], 2),
-                            "server_ms": {"amd": _p50(result["amd_pages"][pg].get("serverMs")),
-                                          "reference": _p50(result["ref_pages"][pg].get("serverMs"))}}
+            per_page[pg] = {"amd": round(a["p50"], 3), "amd_p95": round(a["p95"], 3),
+                            "requests": {"amd": result["amd_pages"][pg]["requestsPerClick"]},
+                            "server_ms": {"amd": _p50(result["amd_pages"][pg].get("serverMs"))}}
+            if args.full:
+                r = summarize(result["ref_pages"][pg]["latencies"])
+                per_page[pg].update(reference=round(r["p50"], 3), reference_p95=round(r["p95"], 3),
+                                    speedup=round(r["p50"] / a["p50"], 2))
+                per_page[pg]["requests"]["reference"] = result["ref_pages"][pg]["requestsPerClick"]
+                per_page[pg]["server_ms"]["reference"] = _p50(result["ref_pages"][pg].get("serverMs"))
         value = sum(per_page[pg]["amd"] for pg in pages) / len(pages)
-        ref_value = sum(per_page[pg]["reference"] for pg in pages) / len(pages)
+        # What every run reports: the headline figure and what it was measured on.
         line = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -282,7 +317,7 @@ def main(argv=None) -> int:
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": False,
             "scaling": "weak",
-            "vs_baseline": round(value / ref_value, 4),
+            "full": args.full,
             "value_definition": "mean over the 5 pages of the p50 latency of that page's Refresh click "
                                 "(data committed + page rebuilt and rendered); one step = one click per page",
             # The metric is a dashboard latency, not a numeric computation.
@@ -303,6 +338,19 @@ def main(argv=None) -> int:
                 "control_plane": args.control_plane,
             },
             "per_page_refresh_p50_ms": per_page,
+            # Rows the last timed click of each page rendered (what --dump-outputs writes).
+            "table_rows": {pg: result["amd_pages"][pg]["tableRows"] for pg in pages},
+            "live_telemetry": bool(result["scrapes"]) and n_nodes > 0,
+            "telemetry_source": "native amdgpu-exporter (C++/HIP) scraped every 15 s (deploy/exporter ServiceMonitor interval)" if exporter else "synthetic",
+            "host": socket.gethostname(),
+        }
+    if info.is_main and args.full:
+        amd_s = summarize(result["amd"]["latencies"])
+        ref_s = summarize(result["ref"]["latencies"])
+        rows = result["amd"]["rows"]
+        ref_value = sum(per_page[pg]["reference"] for pg in pages) / len(pages)
+        line.update({
+            "vs_baseline": round(value / ref_value, 4),
             "baseline": {"schedule": "reference plugin request schedule replayed on the same server, per page as wired",
                          "value_ms": round(ref_value, 3)},
             # Secondary: every page's data + every view in one refresh (no
@@ -391,10 +439,8 @@ def main(argv=None) -> int:
             "replay_fetched_same_rows": all(
                 rows[k] == result["ref"]["rows"][k]
                 for k in ("gpuNodes", "gpuPods", "gpusMonitored", "podTableRows", "detailSections")),
-            "live_telemetry": bool(result["scrapes"]) and n_nodes > 0,
-            "telemetry_source": "native amdgpu-exporter (C++/HIP) scraped every 15 s (deploy/exporter ServiceMonitor interval)" if exporter else "synthetic",
-            "host": socket.gethostname(),
-        }
+        })
+    if info.is_main:
         print(json.dumps(line), flush=True)
         if args.out:
             with open(args.out, "w") as f:

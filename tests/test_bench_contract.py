@@ -78,7 +78,7 @@ def _check(line, n):
 
 
 def test_bench_single_rank():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--rtt-ms", "10"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--rtt-ms", "10"], cwd=ROOT,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -86,10 +86,41 @@ def test_bench_single_rank():
     _check(lines[0], 1)
 
 
+def test_plain_run_reports_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: warm-up, the timed steps, one line with the headline keys and none of the secondary figures;
+    --dump-outputs writes the rows each page's last timed click rendered, the same on every run."""
+    import numpy as np
+
+    rows = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--rtt-ms", "5",
+                            "--dump-outputs", str(tmp_path / d)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        line = lines[0]
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(line)
+        assert line["full"] is False and line["steps"] == 3 and line["unit"] == "ms" and line["dtype"] == "n/a"
+        assert 0 < line["value"] < 1000 and line["ms_per_step"] > 0
+        pp = line["per_page_refresh_p50_ms"]
+        assert abs(line["value"] - sum(v["amd"] for v in pp.values()) / 5) < 1e-2
+        # three timed steps of five clicks each, at least one 5 ms round trip per click
+        assert all(v["requests"]["amd"] >= 1 for v in pp.values()) and line["ms_per_step"] > 5 * 5
+        for moved in ("vs_baseline", "baseline", "all_pages_refresh", "cold_open_per_page_p50_ms", "render_per_page",
+                      "route_switch_p50_ms", "detail_open", "rendered"):
+            assert moved not in line, moved
+        assert os.listdir(tmp_path / d) == ["table_rows.npy"]
+        out = np.load(tmp_path / d / "table_rows.npy")
+        assert out.dtype == np.float64 and out.shape == (5,)
+        assert out.tolist() == [float(line["table_rows"][k]) for k in ("overview", "devicePlugins", "nodes", "pods", "metrics")]
+        rows.append(out)
+    assert (rows[0] == rows[1]).all() and rows[0].sum() > 0
+
+
 def test_bench_node_exporter_only_cluster_is_one_wave():
     """A Prometheus with node-exporter's amdgpu hwmon series only (the fallback source): every GPU is monitored and
     GPU Nodes / Metrics cold-open in one wave — one query (Metrics: plus its range query), no second cluster-wide read."""
-    r = subprocess.run([sys.executable, "bench.py", "--nodes", "2", "--source", "node-exporter", "--steps", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--nodes", "2", "--source", "node-exporter", "--steps", "2",
                         "--warmup", "1", "--rtt-ms", "5", "--no-burn"], cwd=ROOT, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -104,7 +135,7 @@ def test_bench_node_exporter_only_cluster_is_one_wave():
 def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--full", "--gpus", "2",
                         "--steps", "4", "--warmup", "1", "--rtt-ms", "10"], cwd=ROOT, capture_output=True, text=True,
                        timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -115,8 +146,8 @@ def test_bench_two_ranks_gloo():
 
 @pytest.mark.parametrize("n", [4])
 def test_bench_node_override(n):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--rtt-ms", "10", "--nodes", str(n)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--rtt-ms", "10",
+                        "--nodes", str(n)], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_lines(r.stdout)[0]
     assert line["config"]["nodes"] == n and line["rendered"]["gpu_nodes"] == n
@@ -128,7 +159,7 @@ def test_detail_pages_cost_one_node_of_telemetry_whatever_the_cluster_size():
     # nodes, where the cluster-wide snapshot grows with the GPU count.
     out = {}
     for n in (1, 16):
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--rtt-ms", "5",
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--rtt-ms", "5",
                             "--nodes", str(n)], cwd=ROOT, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-3000:]
         out[n] = _json_lines(r.stdout)[0]["detail_open"]

@@ -16,6 +16,7 @@ Prometheus scrapes the exporter) → the plugin's shipped data layer over HTTP (
 Reference analog: none — the reference's tests mock the metrics layer (src/components/MetricsPage.test.tsx).
 """
 import html
+import os
 import re
 import time
 
@@ -78,6 +79,10 @@ def test_dashboard_shows_exactly_what_the_exporter_reports(tmp_path):
 def test_dashboard_shows_the_real_mi355x(tmp_path):
     from headlamp_intel_gpu_plugin_amd.ops import probe
 
+    used = f"/sys/bus/pci/devices/{probe.device_info(0)['bdf']}/mem_info_vram_used"
+    if not os.path.exists(used):
+        # the page then shows "—" for HBM used, and this test reads that figure back
+        pytest.skip(f"needs the amdgpu sysfs file mem_info_vram_used, {used} is not there")
     before = probe.sample(0)
     row = dashboard_row(lambda: probe.sample(0), tmp_path)
     after = probe.sample(0)

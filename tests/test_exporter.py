@@ -3,6 +3,7 @@
 CPU tests run the binary with no GPU (it must still answer, with no GPU series);
 the GPU test checks real MI355X series and the single-device relabelling mode.
 """
+import glob
 import os
 import re
 import shutil
@@ -84,8 +85,6 @@ def test_exporter_reports_mi355x(exe):
     # HIP's device name is empty on this ROCm; the probe names the board from sysfs / device id.
     assert labels["card_model"] == "AMD Instinct MI355X", labels
     assert re.fullmatch(r"[0-9A-F]{16}", labels["serial_number"]), labels
-    slow = [v for n, l, v in rows if n == "gpu_junction_temperature_slowdown" and l["gpu_id"] == "0"]
-    assert slow and 90 <= slow[0] <= 120, slow  # amd-smi: slowdown_hotspot_temperature 100 C
     part = [l for n, l, _ in rows if n == "gpu_partition_info"]
     assert part and part[0]["compute_partition"] in {"SPX", "DPX", "QPX", "CPX"}, part
     assert part[0]["memory_partition"] in {"NPS1", "NPS2", "NPS4", "NPS8"}, part
@@ -94,6 +93,19 @@ def test_exporter_reports_mi355x(exe):
     ids = {l["gpu_id"] for n, l, _ in parse_exposition(one.stdout)}
     assert ids == {"7"}
     time.sleep(0)
+
+
+@pytest.mark.gpu
+def test_exporter_reports_the_junction_slowdown_limit(exe):
+    from headlamp_intel_gpu_plugin_amd.ops import probe
+
+    hwmon = f"/sys/bus/pci/devices/{probe.device_info(0)['bdf']}/hwmon"
+    if not glob.glob(f"{hwmon}/hwmon*/temp*_crit"):
+        pytest.skip(f"needs a hwmon temperature limit file (temp*_crit), {hwmon} has none")
+    r = subprocess.run([exe, "--once", "--hostname", "n0"], capture_output=True, text=True, timeout=60)
+    rows = parse_exposition(r.stdout)
+    slow = [v for n, l, v in rows if n == "gpu_junction_temperature_slowdown" and l["gpu_id"] == "0"]
+    assert slow and 90 <= slow[0] <= 120, slow  # amd-smi: slowdown_hotspot_temperature 100 C
 
 
 def test_exporter_process_and_device_relabel(exe):

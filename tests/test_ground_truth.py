@@ -143,6 +143,8 @@ def test_ras_counters_equal_the_sysfs_sums(exe, dev):
 
 def test_hbm_in_use_between_two_direct_reads(exe, dev):
     info, d = dev
+    if not os.path.exists(f"{d}/mem_info_vram_used"):
+        pytest.skip(f"needs the amdgpu sysfs file mem_info_vram_used, {d} has none")
     before = int(_read(f"{d}/mem_info_vram_used"))
     rows = _scrape(exe)
     after = int(_read(f"{d}/mem_info_vram_used"))

@@ -5,6 +5,7 @@ The MI355X tree is rebuilt from a capture of a real card's ``ras/`` directory
 ``aca_*`` files of ``ue/ce/de`` counts, ``event_state``, ``features`` and an
 empty ``gpu_vram_bad_pages``. Pure file parsing, so these run on the CPU.
 """
+import glob
 import os
 import shutil
 
@@ -96,6 +97,9 @@ def test_exporter_help_declares_ecc_counters(tmp_path):
 @pytest.mark.gpu
 def test_real_card_reports_ras_counters(native):
     assert native.available()
+    ras = f"/sys/bus/pci/devices/{native.device_info(0)['bdf']}/ras"
+    if not glob.glob(f"{ras}/aca_*") and not glob.glob(f"{ras}/*_err_count"):
+        pytest.skip(f"needs the amdgpu RAS counter files (aca_* or *_err_count), {ras} has none")
     s = native.sample(0)
     # An MI355X exposes ras/aca_* (tests/fixtures/mi355x/sysfs_ras.txt): the
     # counters are numbers (normally 0), never absent.

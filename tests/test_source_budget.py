@@ -16,8 +16,21 @@ def test_js_sources_pass_lint_js():
     assert "0 findings" in r.stdout
 
 
+#: Directories that hold no source of this project (dependencies, build output, scratch), skipped when walking.
+NOT_SOURCE = {"node_modules", "build", "dist", "dist-offline", "__pycache__", "_ref"}
+
+
 def _tracked(exts):
-    out = subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.split()
+    """The project's sources with these extensions: git's list in a checkout, the tree itself in an exported copy."""
+    try:
+        r = subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True)
+    except OSError:
+        r = None
+    out = r.stdout.split() if r is not None and r.returncode == 0 else []
+    if not out:
+        for d, dirs, files in os.walk(ROOT):
+            dirs[:] = [x for x in dirs if x not in NOT_SOURCE and not x.startswith(".")]
+            out += [os.path.relpath(os.path.join(d, f), ROOT) for f in files]
     return [f for f in out if f.endswith(exts)]
 
 

@@ -47,8 +47,9 @@ def label_of(r):
 
 
 def run(kind, val, args):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--rtt-ms", str(args.rtt_ms)]
+    # --full: the tables need the reference replay, cold opens and render figures next to the headline
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(args.steps),
+           "--warmup", str(args.warmup), "--rtt-ms", str(args.rtt_ms)]
     # hwmon: a cluster whose Prometheus holds node-exporter's amdgpu series only (the plugin's fallback source)
     cmd += ["--nodes", val, "--source", "node-exporter"] if kind == "hwmon" else [f"--{kind}", val]
     if args.extra:
