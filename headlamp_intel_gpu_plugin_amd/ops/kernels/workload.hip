@@ -32,8 +32,19 @@
 //                 neighbouring tiles.
 //   stream_triad  c = a + s·b over fp32, 16-byte accesses, one pass with 4
 //                 vectors per thread and non-temporal stores: 5.78 TB/s.
+//   gemm_mxfp8_nt, quantize_mxfp8 (kernels/gemm_mxfp8.h, design notes there):
+//                 the inference-like load. Block-scaled fp8 GEMM (OCP e4m3,
+//                 one E8M0 scale per 32 along K) on
+//                 v_mfma_scale_f32_16x16x128_f8f6f4 with the 8-phase kernel's
+//                 256×256 tile, LDS-DMA staging and packed epilogue, a
+//                 256×256×128 K-tile and a two-buffer pipeline; and the
+//                 one-pass bf16 → MXFP8 quantiser that makes its operands on
+//                 the device. Measured (profiles/mxfp8_gemm_ab.md): 1167
+//                 TFLOP/s at 8192³ and 1064 at 4096³, level with the
+//                 register-staged bf16 tile (1148 / 1100) and 79 % of the
+//                 8-phase kernel; quantiser 5.2 TB/s at 8192².
 //
-// Both are bounds-safe by construction: the host wrappers reject shapes the
+// All are bounds-safe by construction: the host wrappers reject shapes the
 // tiling does not cover (see ops/workload.py), and every launch is checked.
 //
 // Python binding: CPython C API module `_workload` (bottom of file), taking
@@ -263,19 +274,56 @@ __device__ __forceinline__ int p8_src_row(int kind, int r) {
                   : (r >> 5) * 64 + (kind & 1) * 32 + (r & 31);   // B: wave col r/32, subtile kind-2
 }
 
-__global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* __restrict__ A,
-                                                              const uint16_t* __restrict__ B,
-                                                              uint16_t* __restrict__ C, int M, int N, int K) {
-  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-
+// First row and column of this block's 256² tile of C: XCD remap, then
+// P8_GROUP tile-rows per L2 group.
+__device__ __forceinline__ void p8_tile_origin(int M, int N, int& m0, int& n0) {
   const int tiles_m = M / 256;
   const int tiles_n = N / 256;
   const int wg = xcd_remap(static_cast<int>(blockIdx.x), tiles_m * tiles_n);
   const int span = P8_GROUP * tiles_n;
   const int first_m = (wg / span) * P8_GROUP;
   const int rows_in_group = min(P8_GROUP, tiles_m - first_m);
-  const int m0 = (first_m + (wg % span) % rows_in_group) * 256;
-  const int n0 = ((wg % span) / rows_in_group) * 256;
+  m0 = (first_m + (wg % span) % rows_in_group) * 256;
+  n0 = ((wg % span) / rows_in_group) * 256;
+}
+
+// Packed epilogue of the 256² kernels (guide T21). Wave (wr, wc) owns rows
+// wr·128.., columns wc·64.. of the tile; acc[i][j] holds C[row][4g..4g+3] of
+// its 16×16 tile (i = 16-row group, j = 16-column group), g = lane>>4. Pack
+// to bf16 pairs, then one v_permlane16_swap per dword between the two
+// 16-column tiles of a 32-column subtile (j = 2p, 2p+1) leaves each lane 8
+// CONSECUTIVE columns: lane group g holds columns 16(g&1) + 8(g>>1) .. +7 —
+// one 16-byte store where the plain layout needed sixteen 2-byte ones (the
+// store tail is issue-bound).
+__device__ __forceinline__ void p8_store_c(const f32x4 (&acc)[8][4], uint16_t* __restrict__ C, int N, int m0, int n0,
+                                           int wr, int wc, int lane) {
+  const int g = lane >> 4;
+  const int col16 = (g & 1) * 16 + (g >> 1) * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = m0 + wr * 128 + (i >> 2) * 64 + (i & 3) * 16 + (lane & 15);
+    uint16_t* crow = C + static_cast<size_t>(row) * N + n0 + wc * 64 + col16;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      uint32_t a0 = pack_bf16x2(acc[i][2 * p][0], acc[i][2 * p][1]);
+      uint32_t a1 = pack_bf16x2(acc[i][2 * p][2], acc[i][2 * p][3]);
+      uint32_t b0 = pack_bf16x2(acc[i][2 * p + 1][0], acc[i][2 * p + 1][1]);
+      uint32_t b1 = pack_bf16x2(acc[i][2 * p + 1][2], acc[i][2 * p + 1][3]);
+      // Odd 16-lane rows of the first operand swap with even rows of the second.
+      const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
+      const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+      *reinterpret_cast<u32x4*>(crow + p * 32) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+    }
+  }
+}
+
+__global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* __restrict__ A,
+                                                              const uint16_t* __restrict__ B,
+                                                              uint16_t* __restrict__ C, int M, int N, int K) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+
+  int m0, n0;
+  p8_tile_origin(M, N, m0, n0);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -415,31 +463,11 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* _
 #undef P8_MFMA
 #undef P8_SYNC_MFMA
 
-  // Epilogue (guide T21): acc[i][j] holds C[row][4g..4g+3] of its 16×16 tile,
-  // g = lane>>4. Pack to bf16 pairs, then one v_permlane16_swap per dword
-  // between the two 16-column tiles of a 32-column subtile (j = 2p, 2p+1)
-  // leaves each lane 8 CONSECUTIVE columns: lane group g holds columns
-  // 16(g&1) + 8(g>>1) .. +7 — one 16-byte store where the plain layout
-  // needed sixteen 2-byte ones (the store tail is issue-bound).
-  const int g = lane >> 4;
-  const int col16 = (g & 1) * 16 + (g >> 1) * 8;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = m0 + wr * 128 + (i >> 2) * 64 + (i & 3) * 16 + (lane & 15);
-    uint16_t* crow = C + static_cast<size_t>(row) * N + n0 + wc * 64 + col16;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      uint32_t a0 = pack_bf16x2(acc[i][2 * p][0], acc[i][2 * p][1]);
-      uint32_t a1 = pack_bf16x2(acc[i][2 * p][2], acc[i][2 * p][3]);
-      uint32_t b0 = pack_bf16x2(acc[i][2 * p + 1][0], acc[i][2 * p + 1][1]);
-      uint32_t b1 = pack_bf16x2(acc[i][2 * p + 1][2], acc[i][2 * p + 1][3]);
-      // Odd 16-lane rows of the first operand swap with even rows of the second.
-      const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-      *reinterpret_cast<u32x4*>(crow + p * 32) = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-  }
+  p8_store_c(acc, C, N, m0, n0, wr, wc, lane);
 }
+
+// MXFP8 (e4m3 + E8M0 block scales): gemm_mxfp8_nt, quantize_mxfp8 and their launchers.
+#include "gemm_mxfp8.h"
 
 // One pass, no grid-stride loop: each thread moves TRIAD_U 16-byte vectors,
 // all loads issued before any store (memory-level parallelism), and the
@@ -588,12 +616,44 @@ PyObject* py_triad(PyObject*, PyObject* args) {
   Py_RETURN_NONE;
 }
 
+PyObject* py_gemm_mxfp8(PyObject*, PyObject* args) {
+  unsigned long long a, b, sa, sb, c, stream;  // sa == sb == 0: unscaled
+  int m, n, k;
+  if (!PyArg_ParseTuple(args, "KKKKKiiiK", &a, &b, &sa, &sb, &c, &m, &n, &k, &stream)) return nullptr;
+  const char* err = launch_gemm_mxfp8(reinterpret_cast<void*>(a), reinterpret_cast<void*>(b), reinterpret_cast<void*>(sa),
+                                      reinterpret_cast<void*>(sb), reinterpret_cast<void*>(c), m, n, k,
+                                      reinterpret_cast<hipStream_t>(stream));
+  if (err) {
+    PyErr_SetString(PyExc_RuntimeError, err);
+    return nullptr;
+  }
+  Py_RETURN_NONE;
+}
+
+PyObject* py_quantize_mxfp8(PyObject*, PyObject* args) {
+  unsigned long long x, q, scales, stream;
+  long long rows, k;
+  if (!PyArg_ParseTuple(args, "KKKLLK", &x, &q, &scales, &rows, &k, &stream)) return nullptr;
+  const char* err = launch_quantize_mxfp8(reinterpret_cast<void*>(x), reinterpret_cast<void*>(q),
+                                          reinterpret_cast<void*>(scales), rows, k, reinterpret_cast<hipStream_t>(stream));
+  if (err) {
+    PyErr_SetString(PyExc_RuntimeError, err);
+    return nullptr;
+  }
+  Py_RETURN_NONE;
+}
+
 PyObject* py_tile(PyObject*, PyObject*) { return Py_BuildValue("(iii)", 128, 128, BK); }
 
 PyMethodDef kMethods[] = {
     {"gemm_bf16_nt", py_gemm, METH_VARARGS,
      "gemm_bf16_nt(a, b, c, M, N, K, stream, variant=0): C = A @ B^T (bf16, fp32 acc); variant 0 auto, "
      "1 128x128, 2 256x256 register-staged, 3 256x256 8-phase LDS-DMA."},
+    {"gemm_mxfp8_nt", py_gemm_mxfp8, METH_VARARGS,
+     "gemm_mxfp8_nt(a, b, scale_a, scale_b, c, M, N, K, stream): C = (A*2^(SA-127)) @ (B*2^(SB-127))^T (e4m3 in, "
+     "E8M0 scales per 32 along K or both 0 for none, fp32 acc, bf16 out)."},
+    {"quantize_mxfp8", py_quantize_mxfp8, METH_VARARGS,
+     "quantize_mxfp8(x, q, scales, rows, K, stream): bf16 [rows,K] -> e4m3 [rows,K] + E8M0 [rows,K/32]."},
     {"stream_triad", py_triad, METH_VARARGS, "stream_triad(a, b, c, n, s, stream): c = a + s*b (fp32)."},
     {"tile", py_tile, METH_NOARGS, "(BM, BN, BK) of the GEMM tiling."},
     {nullptr, nullptr, 0, nullptr}};

@@ -2,9 +2,12 @@
 
 * :func:`gemm_bf16_nt` — ``C = A @ B.T`` on MFMA (bf16 in, fp32 accumulate, bf16 out)
 * :func:`stream_triad` — ``c = a + s * b`` (fp32, HBM-bound)
+* :func:`gemm_mxfp8_nt` — the same product on block-scaled fp8 (OCP e4m3 with one
+  E8M0 scale per 32 along K, "MXFP8"), and :func:`quantize_mxfp8`, which makes
+  such operands from bf16 on the device
 * :class:`Burner` — runs a GEMM + triad mix on a side stream for a target
   duration: the synthetic "GPU pod" whose power / HBM / activity the
-  exporter reports.
+  exporter reports (``precision="mxfp8"``: an inference-like fp8 mix).
 
 Shapes are validated on the host before any launch (the kernels assume full
 tiles and 16-byte alignment); there is no PyTorch fallback.
@@ -40,6 +43,8 @@ def _stream_handle(stream: Optional[torch.cuda.Stream], device) -> int:
 #: Kernel variants of gemm_bf16_nt (see kernels/workload.hip): picked by shape
 #: by default; forcing one is for tests and A/B timing.
 GEMM_VARIANTS = {"auto": 0, "tile128": 1, "tile256": 2, "tile256_dma": 3}
+#: Operand precisions of the GEMM in Burner and time_gemm.
+PRECISIONS = ("bf16", "mxfp8")
 
 
 def gemm_bf16_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -73,6 +78,74 @@ def gemm_bf16_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] =
     return out
 
 
+def _check_mx_scales(name: str, scale: torch.Tensor, operand: torch.Tensor) -> None:
+    rows, k = operand.shape
+    if scale.dtype != torch.uint8:
+        raise TypeError(f"{name} must be uint8 (E8M0)")
+    if scale.shape != (rows, k // 32) or scale.device != operand.device:
+        raise ValueError(f"{name} must be [{rows},{k // 32}] (one byte per 32 along K) on its operand's device, "
+                         f"got {tuple(scale.shape)}")
+
+
+def gemm_mxfp8_nt(a: torch.Tensor, b: torch.Tensor, scale_a: Optional[torch.Tensor] = None,
+                  scale_b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """C[M,N] = (A·2^(SA−127)) @ (B·2^(SB−127))^T in bf16, with fp32 accumulation.
+
+    ``a`` [M,K] and ``b`` [N,K] are ``float8_e4m3fn``; ``scale_a`` [M,K/32] and
+    ``scale_b`` [N,K/32] are ``uint8`` E8M0 exponents, one per 32 elements along
+    K, both given or both ``None`` (a plain fp8 GEMM). M and N must be multiples
+    of 256, K of 128, and M·K and N·K below 2^32; ``out`` must be 16-byte aligned.
+    """
+    if a.dtype != torch.float8_e4m3fn or b.dtype != torch.float8_e4m3fn:
+        raise TypeError("gemm_mxfp8_nt expects float8_e4m3fn inputs")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"shape mismatch: A{tuple(a.shape)} B{tuple(b.shape)} (need A[M,K], B[N,K])")
+    m, k = a.shape
+    n = b.shape[0]
+    if m % 256 or n % 256 or k % 128 or m * k >= 2 ** 32 or n * k >= 2 ** 32:
+        raise ValueError(f"gemm_mxfp8_nt needs M%256==0, N%256==0, K%128==0, M*K and N*K < 2^32 (got {m}x{n}x{k})")
+    if (scale_a is None) != (scale_b is None):
+        raise ValueError("give both scale_a and scale_b, or neither")
+    if scale_a is not None:
+        _check_mx_scales("scale_a", scale_a, a)
+        _check_mx_scales("scale_b", scale_b, b)
+        scale_a = scale_a.contiguous()
+        scale_b = scale_b.contiguous()
+    if not (a.is_cuda and b.is_cuda) or a.device != b.device:
+        raise ValueError("A and B must be on the same GPU")
+    a = a.contiguous()
+    b = b.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+    elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != a.device:
+        raise ValueError("out must be a contiguous bfloat16 [M,N] tensor on A's device")
+    native().gemm_mxfp8_nt(a.data_ptr(), b.data_ptr(), scale_a.data_ptr() if scale_a is not None else 0,
+                           scale_b.data_ptr() if scale_b is not None else 0, out.data_ptr(), m, n, k,
+                           _stream_handle(stream, a.device))
+    return out
+
+
+def quantize_mxfp8(x: torch.Tensor, stream: Optional[torch.cuda.Stream] = None):
+    """bf16 [R,K] → (``float8_e4m3fn`` [R,K], ``uint8`` E8M0 scales [R,K/32]) by the OCP MX rule.
+
+    Per block of 32 along K: X = floor(log2(amax)) − 8 clamped to [−127, 127], scale
+    byte X + 127, elements RNE_e4m3(clamp(v·2^−X, ±448)); an all-zero block gets
+    scale byte 127. ``x`` is contiguous and finite, K a multiple of 32.
+    """
+    if x.dtype != torch.bfloat16:
+        raise TypeError("quantize_mxfp8 expects bfloat16")
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % 32 or not x.is_contiguous():
+        raise ValueError(f"quantize_mxfp8 needs a contiguous [R,K] tensor with K%32==0 (got {tuple(x.shape)})")
+    if not x.is_cuda:
+        raise ValueError("x must be on a GPU")
+    rows, k = x.shape
+    q = torch.empty((rows, k), dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty((rows, k // 32), dtype=torch.uint8, device=x.device)
+    native().quantize_mxfp8(x.data_ptr(), q.data_ptr(), scales.data_ptr(), rows, k, _stream_handle(stream, x.device))
+    return q, scales
+
+
 def stream_triad(a: torch.Tensor, b: torch.Tensor, s: float, out: Optional[torch.Tensor] = None,
                  stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """out = a + s * b over contiguous float32 vectors whose length is a multiple of 4."""
@@ -102,10 +175,16 @@ class Burner:
     profiles/r1_diag_graph_sync.md), and the benchmark's timed region is
     bracketed by exactly that call. Callers keep the launch rate low with
     larger kernels instead (bench.py: 2 × 8192³ GEMMs + triad per iteration).
+    ``precision="mxfp8"`` is the inference-like mix: the weight operand is
+    quantised once, and each iteration re-quantises the activation operand
+    once and runs the ``gemms`` GEMMs on MXFP8.
     """
 
     def __init__(self, device: int = 0, size: int = 4096, gemms: int = 4, triad_mb: int = 1024,
-                 graph_iters: int = 0):
+                 graph_iters: int = 0, precision: str = "bf16"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}; one of {PRECISIONS}")
+        self.precision = precision
         self.device = torch.device("cuda", device)
         self.size = size
         self.gemms = gemms
@@ -131,10 +210,21 @@ class Burner:
             z = torch.empty_like(x)
             stream = torch.cuda.Stream(self.device)
 
-            def one_iteration():
-                for _ in range(self.gemms):
-                    gemm_bf16_nt(a, b, out=c, stream=stream)
-                stream_triad(x, y, 0.5, out=z, stream=stream)
+            if self.precision == "mxfp8":
+                stream.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(stream):
+                    bq, bs = quantize_mxfp8(b)  # the weights: once
+
+                def one_iteration():
+                    aq, as_ = quantize_mxfp8(a, stream=stream)
+                    for _ in range(self.gemms):
+                        gemm_mxfp8_nt(aq, bq, as_, bs, out=c, stream=stream)
+                    stream_triad(x, y, 0.5, out=z, stream=stream)
+            else:
+                def one_iteration():
+                    for _ in range(self.gemms):
+                        gemm_bf16_nt(a, b, out=c, stream=stream)
+                    stream_triad(x, y, 0.5, out=z, stream=stream)
 
             with torch.cuda.stream(stream):
                 one_iteration()  # warm-up outside capture (sets kernel attributes once)
@@ -208,20 +298,32 @@ def gemm_tflops(m: int, n: int, k: int, seconds: float) -> float:
     return 2.0 * m * n * k / seconds / 1e12
 
 
-def time_gemm(size: int = 8192, iters: int = 20, device: int = 0, variant: str = "auto") -> float:
-    """Median TFLOP/s of gemm_bf16_nt at size³ (uniform random operands)."""
+def time_gemm(size: int = 8192, iters: int = 20, device: int = 0, variant: str = "auto",
+              precision: str = "bf16") -> float:
+    """Median TFLOP/s of the GEMM at size³ (uniform random operands): gemm_bf16_nt, or with
+    ``precision="mxfp8"`` gemm_mxfp8_nt on the quantised operands (same 2·M·N·K count)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; one of {PRECISIONS}")
     dev = torch.device("cuda", device)
     a = (torch.rand(size, size, device=dev) * 2 - 1).to(torch.bfloat16)
     b = (torch.rand(size, size, device=dev) * 2 - 1).to(torch.bfloat16)
     c = torch.empty_like(a)
+    if precision == "mxfp8":
+        operands = quantize_mxfp8(a) + quantize_mxfp8(b)
+
+        def run():
+            gemm_mxfp8_nt(operands[0], operands[2], operands[1], operands[3], out=c)
+    else:
+        def run():
+            gemm_bf16_nt(a, b, out=c, variant=variant)
     for _ in range(3):
-        gemm_bf16_nt(a, b, out=c, variant=variant)
+        run()
     torch.cuda.synchronize(dev)
     times = []
     for _ in range(iters):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-        gemm_bf16_nt(a, b, out=c, variant=variant)
+        run()
         e.record()
         e.synchronize()
         times.append(s.elapsed_time(e) / 1e3)
