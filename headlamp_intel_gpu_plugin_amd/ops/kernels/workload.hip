@@ -43,6 +43,14 @@
 //                 TFLOP/s at 8192³ and 1064 at 4096³, level with the
 //                 register-staged bf16 tile (1148 / 1100) and 79 % of the
 //                 8-phase kernel; quantiser 5.2 TB/s at 8192².
+//   gemm_mxfp4_nt, quantize_mxfp4 (kernels/gemm_mxfp4.h, design notes there):
+//                 the same pair on block-scaled fp4 (OCP e2m1, two per byte),
+//                 the MFMA's fastest format. The 8-phase kernel's tile,
+//                 staging, counted-vmcnt schedule and epilogue on a
+//                 256×256×256 K-tile, scales staged through LDS. Measured
+//                 (profiles/mxfp4_gemm_ab.md): 4317 TFLOP/s at 8192³ and 3033
+//                 at 4096³ (4276 / 2986 in a second run), 3.8 / 2.9 times
+//                 gemm_mxfp8_nt in the same run; quantiser 4.3 TB/s at 8192².
 //
 // All are bounds-safe by construction: the host wrappers reject shapes the
 // tiling does not cover (see ops/workload.py), and every launch is checked.
@@ -468,6 +476,8 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* _
 
 // MXFP8 (e4m3 + E8M0 block scales): gemm_mxfp8_nt, quantize_mxfp8 and their launchers.
 #include "gemm_mxfp8.h"
+// MXFP4 (e2m1 + E8M0): gemm_mxfp4_nt, quantize_mxfp4, their launchers and Python bindings.
+#include "gemm_mxfp4.h"
 
 // One pass, no grid-stride loop: each thread moves TRIAD_U 16-byte vectors,
 // all loads issued before any store (memory-level parallelism), and the
@@ -654,6 +664,11 @@ PyMethodDef kMethods[] = {
      "E8M0 scales per 32 along K or both 0 for none, fp32 acc, bf16 out)."},
     {"quantize_mxfp8", py_quantize_mxfp8, METH_VARARGS,
      "quantize_mxfp8(x, q, scales, rows, K, stream): bf16 [rows,K] -> e4m3 [rows,K] + E8M0 [rows,K/32]."},
+    {"gemm_mxfp4_nt", py_gemm_mxfp4, METH_VARARGS,
+     "gemm_mxfp4_nt(a, b, scale_a, scale_b, c, M, N, K, stream): the same product on packed e2m1 [rows,K/2] with "
+     "mandatory E8M0 scales per 32 along K; K a multiple of 512."},
+    {"quantize_mxfp4", py_quantize_mxfp4, METH_VARARGS,
+     "quantize_mxfp4(x, q, scales, rows, K, stream): bf16 [rows,K] -> packed e2m1 [rows,K/2] + E8M0 [rows,K/32]."},
     {"stream_triad", py_triad, METH_VARARGS, "stream_triad(a, b, c, n, s, stream): c = a + s*b (fp32)."},
     {"tile", py_tile, METH_NOARGS, "(BM, BN, BK) of the GEMM tiling."},
     {nullptr, nullptr, 0, nullptr}};

@@ -5,9 +5,12 @@
 * :func:`gemm_mxfp8_nt` — the same product on block-scaled fp8 (OCP e4m3 with one
   E8M0 scale per 32 along K, "MXFP8"), and :func:`quantize_mxfp8`, which makes
   such operands from bf16 on the device
+* :func:`gemm_mxfp4_nt` and :func:`quantize_mxfp4` — the same pair on block-scaled
+  fp4 (OCP e2m1, two elements per byte, "MXFP4"), the format with CDNA4's highest
+  matrix rate
 * :class:`Burner` — runs a GEMM + triad mix on a side stream for a target
   duration: the synthetic "GPU pod" whose power / HBM / activity the
-  exporter reports (``precision="mxfp8"``: an inference-like fp8 mix).
+  exporter reports (``precision="mxfp8"`` / ``"mxfp4"``: inference-like mixes).
 
 Shapes are validated on the host before any launch (the kernels assume full
 tiles and 16-byte alignment); there is no PyTorch fallback.
@@ -44,7 +47,7 @@ def _stream_handle(stream: Optional[torch.cuda.Stream], device) -> int:
 #: by default; forcing one is for tests and A/B timing.
 GEMM_VARIANTS = {"auto": 0, "tile128": 1, "tile256": 2, "tile256_dma": 3}
 #: Operand precisions of the GEMM in Burner and time_gemm.
-PRECISIONS = ("bf16", "mxfp8")
+PRECISIONS = ("bf16", "mxfp8", "mxfp4")
 
 
 def gemm_bf16_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -78,8 +81,8 @@ def gemm_bf16_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] =
     return out
 
 
-def _check_mx_scales(name: str, scale: torch.Tensor, operand: torch.Tensor) -> None:
-    rows, k = operand.shape
+def _check_mx_scales(name: str, scale: torch.Tensor, operand: torch.Tensor, per_byte: int = 1) -> None:
+    rows, k = operand.shape[0], operand.shape[1] * per_byte  # per_byte: elements in one byte of the operand
     if scale.dtype != torch.uint8:
         raise TypeError(f"{name} must be uint8 (E8M0)")
     if scale.shape != (rows, k // 32) or scale.device != operand.device:
@@ -146,6 +149,65 @@ def quantize_mxfp8(x: torch.Tensor, stream: Optional[torch.cuda.Stream] = None):
     return q, scales
 
 
+def gemm_mxfp4_nt(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                  out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """C[M,N] = (A·2^(SA−127)) @ (B·2^(SB−127))^T in bf16, on packed fp4 with fp32 accumulation.
+
+    ``a`` [M,K/2] and ``b`` [N,K/2] are ``uint8`` holding two OCP e2m1 elements per byte,
+    element 2i in bits 0-3 of byte i; ``scale_a`` [M,K/32] and ``scale_b`` [N,K/32] are
+    ``uint8`` E8M0 exponents, one per 32 elements along K, and mandatory. M and N must be
+    multiples of 256, K of 512 (the kernel consumes 256-element K-tiles in pairs), and
+    M·K/2 and N·K/2 below 2^32; ``out`` must be 16-byte aligned.
+    """
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise TypeError("gemm_mxfp4_nt expects uint8 inputs (two e2m1 elements per byte)")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"shape mismatch: A{tuple(a.shape)} B{tuple(b.shape)} (need A[M,K/2], B[N,K/2])")
+    m, k = a.shape[0], 2 * a.shape[1]
+    n = b.shape[0]
+    if m % 256 or n % 256 or k % 512 or m * k // 2 >= 2 ** 32 or n * k // 2 >= 2 ** 32:
+        raise ValueError(f"gemm_mxfp4_nt needs M%256==0, N%256==0, K%512==0, M*K/2 and N*K/2 < 2^32 (got {m}x{n}x{k})")
+    if scale_a is None or scale_b is None:
+        raise ValueError("gemm_mxfp4_nt needs both scale_a and scale_b")
+    _check_mx_scales("scale_a", scale_a, a, per_byte=2)
+    _check_mx_scales("scale_b", scale_b, b, per_byte=2)
+    if not (a.is_cuda and b.is_cuda) or a.device != b.device:
+        raise ValueError("A and B must be on the same GPU")
+    a, b, scale_a, scale_b = a.contiguous(), b.contiguous(), scale_a.contiguous(), scale_b.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+    elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != a.device:
+        raise ValueError("out must be a contiguous bfloat16 [M,N] tensor on A's device")
+    native().gemm_mxfp4_nt(a.data_ptr(), b.data_ptr(), scale_a.data_ptr(), scale_b.data_ptr(), out.data_ptr(), m, n, k,
+                           _stream_handle(stream, a.device))
+    return out
+
+
+def quantize_mxfp4(x: torch.Tensor, stream: Optional[torch.cuda.Stream] = None):
+    """bf16 [R,K] → (``uint8`` packed e2m1 [R,K/2], ``uint8`` E8M0 scales [R,K/32]) by the OCP MX rule.
+
+    Per block of 32 along K: X = floor(log2(amax)) − 2 clamped to [−127, 127], scale byte
+    X + 127, elements RNE_e2m1(clamp(v·2^−X, ±6)) with the sign of v kept (a negative value
+    that rounds to zero is −0); an all-zero block gets scale byte 127. Element 2i is in bits
+    0-3 of byte i. ``x`` is contiguous and finite, K a multiple of 32.
+    """
+    if x.dtype != torch.bfloat16:
+        raise TypeError("quantize_mxfp4 expects bfloat16")
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % 32 or not x.is_contiguous():
+        raise ValueError(f"quantize_mxfp4 needs a contiguous [R,K] tensor with K%32==0 (got {tuple(x.shape)})")
+    if not x.is_cuda:
+        raise ValueError("x must be on a GPU")
+    rows, k = x.shape
+    q = torch.empty((rows, k // 2), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((rows, k // 32), dtype=torch.uint8, device=x.device)
+    native().quantize_mxfp4(x.data_ptr(), q.data_ptr(), scales.data_ptr(), rows, k, _stream_handle(stream, x.device))
+    return q, scales
+
+
+#: The block-scaled precisions: (quantiser, GEMM) with one calling convention.
+_MX = {"mxfp8": (quantize_mxfp8, gemm_mxfp8_nt), "mxfp4": (quantize_mxfp4, gemm_mxfp4_nt)}
+
+
 def stream_triad(a: torch.Tensor, b: torch.Tensor, s: float, out: Optional[torch.Tensor] = None,
                  stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """out = a + s * b over contiguous float32 vectors whose length is a multiple of 4."""
@@ -175,9 +237,9 @@ class Burner:
     profiles/r1_diag_graph_sync.md), and the benchmark's timed region is
     bracketed by exactly that call. Callers keep the launch rate low with
     larger kernels instead (bench.py: 2 × 8192³ GEMMs + triad per iteration).
-    ``precision="mxfp8"`` is the inference-like mix: the weight operand is
-    quantised once, and each iteration re-quantises the activation operand
-    once and runs the ``gemms`` GEMMs on MXFP8.
+    ``precision="mxfp8"`` and ``"mxfp4"`` are the inference-like mixes: the
+    weight operand is quantised once, and each iteration re-quantises the
+    activation operand once and runs the ``gemms`` GEMMs on MXFP8 / MXFP4.
     """
 
     def __init__(self, device: int = 0, size: int = 4096, gemms: int = 4, triad_mb: int = 1024,
@@ -210,15 +272,16 @@ class Burner:
             z = torch.empty_like(x)
             stream = torch.cuda.Stream(self.device)
 
-            if self.precision == "mxfp8":
+            if self.precision in _MX:
+                quantise, gemm = _MX[self.precision]
                 stream.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(stream):
-                    bq, bs = quantize_mxfp8(b)  # the weights: once
+                    bq, bs = quantise(b)  # the weights: once
 
                 def one_iteration():
-                    aq, as_ = quantize_mxfp8(a, stream=stream)
+                    aq, as_ = quantise(a, stream=stream)
                     for _ in range(self.gemms):
-                        gemm_mxfp8_nt(aq, bq, as_, bs, out=c, stream=stream)
+                        gemm(aq, bq, as_, bs, out=c, stream=stream)
                     stream_triad(x, y, 0.5, out=z, stream=stream)
             else:
                 def one_iteration():
@@ -301,18 +364,19 @@ def gemm_tflops(m: int, n: int, k: int, seconds: float) -> float:
 def time_gemm(size: int = 8192, iters: int = 20, device: int = 0, variant: str = "auto",
               precision: str = "bf16") -> float:
     """Median TFLOP/s of the GEMM at size³ (uniform random operands): gemm_bf16_nt, or with
-    ``precision="mxfp8"`` gemm_mxfp8_nt on the quantised operands (same 2·M·N·K count)."""
+    ``precision="mxfp8"`` / ``"mxfp4"`` that precision's GEMM on the quantised operands (same 2·M·N·K count)."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}; one of {PRECISIONS}")
     dev = torch.device("cuda", device)
     a = (torch.rand(size, size, device=dev) * 2 - 1).to(torch.bfloat16)
     b = (torch.rand(size, size, device=dev) * 2 - 1).to(torch.bfloat16)
     c = torch.empty_like(a)
-    if precision == "mxfp8":
-        operands = quantize_mxfp8(a) + quantize_mxfp8(b)
+    if precision in _MX:
+        quantise, gemm = _MX[precision]
+        operands = quantise(a) + quantise(b)
 
         def run():
-            gemm_mxfp8_nt(operands[0], operands[2], operands[1], operands[3], out=c)
+            gemm(operands[0], operands[2], operands[1], operands[3], out=c)
     else:
         def run():
             gemm_bf16_nt(a, b, out=c, variant=variant)

@@ -91,7 +91,7 @@ def main():
     ap.add_argument("--hz", type=float, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--no-burn", action="store_true")
-    ap.add_argument("--precision", default="bf16", help="GEMM operands of the workload pod: bf16 or mxfp8")
+    ap.add_argument("--precision", default="bf16", help="GEMM operands of the workload pod: bf16, mxfp8 or mxfp4")
     ap.add_argument("--sysfs-only", action="store_true", help="run the daemon as the DaemonSet does (no HIP)")
     ap.add_argument("--slow", type=int, default=0, help="slow-loris peers")
     ap.add_argument("--stalled", type=int, default=0, help="peers that never read the response")
