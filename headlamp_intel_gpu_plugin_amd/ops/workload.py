@@ -8,9 +8,12 @@
 * :func:`gemm_mxfp4_nt` and :func:`quantize_mxfp4` — the same pair on block-scaled
   fp4 (OCP e2m1, two elements per byte, "MXFP4"), the format with CDNA4's highest
   matrix rate
+* :func:`gemm_mxfp4_skinny_nt` — the MXFP4 product for a decode batch of 1-64 rows:
+  weights streamed once from HBM, K split over blocks, ordered reduction
 * :class:`Burner` — runs a GEMM + triad mix on a side stream for a target
   duration: the synthetic "GPU pod" whose power / HBM / activity the
-  exporter reports (``precision="mxfp8"`` / ``"mxfp4"``: inference-like mixes).
+  exporter reports (``precision="mxfp8"`` / ``"mxfp4"``: inference-like mixes;
+  ``batch=``: the decode mix).
 
 Shapes are validated on the host before any launch (the kernels assume full
 tiles and 16-byte alignment); there is no PyTorch fallback.
@@ -204,6 +207,67 @@ def quantize_mxfp4(x: torch.Tensor, stream: Optional[torch.cuda.Stream] = None):
     return q, scales
 
 
+#: ``split_k=0`` keeps (N/128)·split_k at or below this multiple of the CU count
+#: (measured: profiles/mxfp4_skinny_ab.md).
+SKINNY_CU_MULTIPLE = 1
+
+
+def skinny_split_k(n: int, k: int, device) -> int:
+    """The split ``gemm_mxfp4_skinny_nt`` picks for ``split_k=0``: the largest divisor of K/256 that keeps
+    (N/128)·split_k at or below ``SKINNY_CU_MULTIPLE`` times the device's CU count."""
+    limit = SKINNY_CU_MULTIPLE * torch.cuda.get_device_properties(device).multi_processor_count // (n // 128)
+    return max((d for d in range(1, k // 256 + 1) if (k // 256) % d == 0 and d <= limit), default=1)
+
+
+def gemm_mxfp4_skinny_nt(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                         out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                         split_k: int = 0, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The product of :func:`gemm_mxfp4_nt` for a decode batch: 1 ≤ M ≤ 64 (any value), N a multiple of 128,
+    K of 256, N·K/2 below 2^32; operands and scales in the same formats.
+
+    K is split over ``split_k`` blocks (a divisor of K/256; 0: :func:`skinny_split_k`) whose fp32 partial sums
+    go to ``workspace`` (float32, at least split_k·M·N elements, allocated on the launch stream when absent) and
+    are added in ascending order by a second kernel, so the result is bit-identical from run to run.
+    ``out`` and ``workspace`` must be 16-byte aligned.
+    """
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise TypeError("gemm_mxfp4_skinny_nt expects uint8 inputs (two e2m1 elements per byte)")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"shape mismatch: A{tuple(a.shape)} B{tuple(b.shape)} (need A[M,K/2], B[N,K/2])")
+    m, k = a.shape[0], 2 * a.shape[1]
+    n = b.shape[0]
+    if not 1 <= m <= 64 or n == 0 or n % 128 or k == 0 or k % 256 or n * k // 2 >= 2 ** 32:
+        raise ValueError(f"gemm_mxfp4_skinny_nt needs 1<=M<=64, N%128==0, K%256==0, N*K/2 < 2^32 (got {m}x{n}x{k})")
+    if split_k < 0 or (split_k and (k // 256) % split_k):
+        raise ValueError(f"split_k must divide K/256 = {k // 256} (got {split_k})")
+    if scale_a is None or scale_b is None:
+        raise ValueError("gemm_mxfp4_skinny_nt needs both scale_a and scale_b")
+    _check_mx_scales("scale_a", scale_a, a, per_byte=2)
+    _check_mx_scales("scale_b", scale_b, b, per_byte=2)
+    if not (a.is_cuda and b.is_cuda) or a.device != b.device:
+        raise ValueError("A and B must be on the same GPU")
+    a, b, scale_a, scale_b = a.contiguous(), b.contiguous(), scale_a.contiguous(), scale_b.contiguous()
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+    elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != a.device:
+        raise ValueError("out must be a contiguous bfloat16 [M,N] tensor on A's device")
+    split_k = split_k or skinny_split_k(n, k, a.device)
+    s = stream if stream is not None else torch.cuda.current_stream(a.device)
+    if split_k == 1:
+        workspace = None
+    elif workspace is None:
+        with torch.cuda.stream(s):
+            workspace = torch.empty(split_k * m * n, dtype=torch.float32, device=a.device)
+    elif (workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != a.device
+          or workspace.numel() < split_k * m * n):
+        raise ValueError(f"workspace must be a contiguous float32 tensor of at least split_k*M*N = "
+                         f"{split_k * m * n} elements on A's device")
+    native().gemm_mxfp4_skinny_nt(a.data_ptr(), b.data_ptr(), scale_a.data_ptr(), scale_b.data_ptr(), out.data_ptr(),
+                                  m, n, k, split_k, workspace.data_ptr() if workspace is not None else 0,
+                                  workspace.numel() * 4 if workspace is not None else 0, int(s.cuda_stream))
+    return out
+
+
 #: The block-scaled precisions: (quantiser, GEMM) with one calling convention.
 _MX = {"mxfp8": (quantize_mxfp8, gemm_mxfp8_nt), "mxfp4": (quantize_mxfp4, gemm_mxfp4_nt)}
 
@@ -240,13 +304,20 @@ class Burner:
     ``precision="mxfp8"`` and ``"mxfp4"`` are the inference-like mixes: the
     weight operand is quantised once, and each iteration re-quantises the
     activation operand once and runs the ``gemms`` GEMMs on MXFP8 / MXFP4.
+    ``batch`` (1..64, ``precision="mxfp4"`` only, ``size`` a multiple of 256) is
+    the decode mix: the activation operand is ``[batch, size]`` and the GEMMs
+    are :func:`gemm_mxfp4_skinny_nt`, which stream the weights from HBM.
     """
 
     def __init__(self, device: int = 0, size: int = 4096, gemms: int = 4, triad_mb: int = 1024,
-                 graph_iters: int = 0, precision: str = "bf16"):
+                 graph_iters: int = 0, precision: str = "bf16", batch: Optional[int] = None):
         if precision not in PRECISIONS:
             raise ValueError(f"unknown precision {precision!r}; one of {PRECISIONS}")
+        if batch is not None and (precision != "mxfp4" or not 1 <= batch <= 64 or size % 256):
+            raise ValueError(f"batch needs precision='mxfp4', 1 <= batch <= 64 and size%256==0 "
+                             f"(got {precision!r}, batch {batch}, size {size})")
         self.precision = precision
+        self.batch = batch
         self.device = torch.device("cuda", device)
         self.size = size
         self.gemms = gemms
@@ -264,7 +335,7 @@ class Burner:
         try:
             torch.cuda.set_device(self.device)
             g = torch.Generator(device=self.device).manual_seed(0)
-            a = torch.randn(self.size, self.size, device=self.device, dtype=torch.bfloat16, generator=g)
+            a = torch.randn(self.batch or self.size, self.size, device=self.device, dtype=torch.bfloat16, generator=g)
             b = torch.randn(self.size, self.size, device=self.device, dtype=torch.bfloat16, generator=g)
             c = torch.empty_like(a)
             x = torch.rand(self.triad_n, device=self.device, generator=g)
@@ -277,6 +348,12 @@ class Burner:
                 stream.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(stream):
                     bq, bs = quantise(b)  # the weights: once
+                    if self.batch:  # decode: the skinny kernel, split and workspace fixed once
+                        split = skinny_split_k(self.size, self.size, self.device)
+                        ws = torch.empty(split * self.batch * self.size, dtype=torch.float32, device=self.device)
+
+                        def gemm(aq, bq, as_, bs, out, stream):
+                            gemm_mxfp4_skinny_nt(aq, bq, as_, bs, out=out, stream=stream, split_k=split, workspace=ws)
 
                 def one_iteration():
                     aq, as_ = quantise(a, stream=stream)
@@ -393,6 +470,54 @@ def time_gemm(size: int = 8192, iters: int = 20, device: int = 0, variant: str =
         times.append(s.elapsed_time(e) / 1e3)
     times.sort()
     return gemm_tflops(size, size, size, times[len(times) // 2])
+
+
+def time_gemm_skinny(m: int, n: int, k: int, iters: int = 20, device: int = 0, split_k: int = 0,
+                     padded: bool = False) -> float:
+    """Median TB/s of gemm_mxfp4_skinny_nt over the bytes it must move (B, SB, A, SA, C) at a decode shape.
+
+    The weights rotate over enough distinct buffers to exceed 512 MiB, twice the 256 MiB Infinity Cache, so the
+    figure is HBM bandwidth. Each sample is one pass over all buffers between two events, enqueued behind a
+    long triad so the launches are back to back on the device, divided by the number of buffers.
+    ``padded=True`` times the other route instead: A zero-padded to 256 rows through gemm_mxfp4_nt, over the
+    same buffers and the same byte count.
+    """
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev).manual_seed(m + n + k)
+    rand = lambda lo, hi, *shape: torch.randint(lo, hi, shape, device=dev, dtype=torch.uint8, generator=g)  # noqa: E731
+    count = (512 << 20) // (n * k // 2) + 1
+    weights = [(rand(0, 256, n, k // 2), rand(120, 135, n, k // 32)) for _ in range(count)]
+    rows = 256 if padded else m
+    a, sa = torch.zeros(rows, k // 2, device=dev, dtype=torch.uint8), rand(120, 135, rows, k // 32)
+    a[:m] = rand(0, 256, m, k // 2)
+    c = torch.empty(rows, n, device=dev, dtype=torch.bfloat16)
+    split = 1 if padded else split_k or skinny_split_k(n, k, dev)
+    ws = torch.empty(split * m * n, device=dev, dtype=torch.float32) if split > 1 else None
+    x = torch.rand(1 << 28, device=dev)
+    y = torch.rand(1 << 28, device=dev)
+    z = torch.empty_like(x)
+
+    def one_pass():
+        for b, sb in weights:
+            if padded:
+                gemm_mxfp4_nt(a, b, sa, sb, out=c)
+            else:
+                gemm_mxfp4_skinny_nt(a, b, sa, sb, out=c, split_k=split, workspace=ws)
+
+    one_pass()
+    torch.cuda.synchronize(dev)
+    times = []
+    for _ in range(iters):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        stream_triad(x, y, 0.5, out=z)  # ~0.6 ms: the pass below is enqueued before the device reaches it
+        s.record()
+        one_pass()
+        e.record()
+        e.synchronize()
+        times.append(s.elapsed_time(e) / 1e3 / count)
+    times.sort()
+    moved = n * k // 2 + n * k // 32 + m * k // 2 + m * k // 32 + m * n * 2
+    return moved / times[len(times) // 2] / 1e12
 
 
 def time_triad(mb: int = 2048, iters: int = 20, device: int = 0) -> float:

@@ -92,6 +92,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--no-burn", action="store_true")
     ap.add_argument("--precision", default="bf16", help="GEMM operands of the workload pod: bf16, mxfp8 or mxfp4")
+    ap.add_argument("--batch", type=int, default=None,
+                    help="decode mix: activation rows (1..64) through the skinny MXFP4 kernel; needs --precision mxfp4")
     ap.add_argument("--sysfs-only", action="store_true", help="run the daemon as the DaemonSet does (no HIP)")
     ap.add_argument("--slow", type=int, default=0, help="slow-loris peers")
     ap.add_argument("--stalled", type=int, default=0, help="peers that never read the response")
@@ -103,7 +105,8 @@ def main():
     if not a.no_burn:
         from headlamp_intel_gpu_plugin_amd.ops.workload import Burner
 
-        burner = Burner(device=0, size=8192, gemms=2, triad_mb=512, precision=a.precision).start()
+        burner = Burner(device=0, size=8192, gemms=2, triad_mb=512, precision=a.precision,
+                        batch=a.batch).start()
     lat, errors, rss, power, gfx = [], 0, [], [], []
     t_end = time.monotonic() + a.seconds
     next_report = time.monotonic() + 15
