@@ -63,6 +63,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
@@ -480,6 +481,8 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* _
 #include "gemm_mxfp4.h"
 // MXFP4 decode (M ≤ 64): gemm_mxfp4_skinny, its split-K reduce, launcher and Python binding.
 #include "gemm_mxfp4_skinny.h"
+// Decode attention over a bf16 KV cache: attn_decode, its split-KV combine, launcher and Python binding.
+#include "attn_decode.h"
 
 // One pass, no grid-stride loop: each thread moves TRIAD_U 16-byte vectors,
 // all loads issued before any store (memory-level parallelism), and the
@@ -670,6 +673,7 @@ PyMethodDef kMethods[] = {
      "gemm_mxfp4_nt(a, b, scale_a, scale_b, c, M, N, K, stream): the same product on packed e2m1 [rows,K/2] with "
      "mandatory E8M0 scales per 32 along K; K a multiple of 512."},
     {"gemm_mxfp4_skinny_nt", py_gemm_mxfp4_skinny, METH_VARARGS, kSkinnyDoc},
+    {"attn_decode_bf16", py_attn_decode, METH_VARARGS, kAttnDecodeDoc},
     {"quantize_mxfp4", py_quantize_mxfp4, METH_VARARGS,
      "quantize_mxfp4(x, q, scales, rows, K, stream): bf16 [rows,K] -> packed e2m1 [rows,K/2] + E8M0 [rows,K/32]."},
     {"stream_triad", py_triad, METH_VARARGS, "stream_triad(a, b, c, n, s, stream): c = a + s*b (fp32)."},

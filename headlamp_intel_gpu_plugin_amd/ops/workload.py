@@ -10,10 +10,13 @@
   matrix rate
 * :func:`gemm_mxfp4_skinny_nt` — the MXFP4 product for a decode batch of 1-64 rows:
   weights streamed once from HBM, K split over blocks, ordered reduction
+* :func:`attn_decode_bf16` — decode attention ``softmax(q·Kᵀ)·V`` of one new token per
+  sequence over a bf16 KV cache with grouped query heads: the cache streamed once from
+  HBM, the keys split over blocks, partials merged in a fixed order
 * :class:`Burner` — runs a GEMM + triad mix on a side stream for a target
   duration: the synthetic "GPU pod" whose power / HBM / activity the
   exporter reports (``precision="mxfp8"`` / ``"mxfp4"``: inference-like mixes;
-  ``batch=``: the decode mix).
+  ``batch=``: the decode mix; ``context=``: with attention over a KV cache).
 
 Shapes are validated on the host before any launch (the kernels assume full
 tiles and 16-byte alignment); there is no PyTorch fallback.
@@ -268,6 +271,84 @@ def gemm_mxfp4_skinny_nt(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor
     return out
 
 
+#: ``split_kv=0`` keeps B·Hkv·split_kv at or below this multiple of the CU count and every slice at least
+#: ``ATTN_MIN_SLICE`` keys long (measured: profiles/attn_decode_ab.md).
+ATTN_CU_MULTIPLE = 1
+ATTN_MIN_SLICE = 512
+
+
+def attn_split_kv(b: int, hkv: int, s_max: int, device) -> int:
+    """The split ``attn_decode_bf16`` picks for ``split_kv=0``: the largest that keeps B·Hkv·split at or below
+    ``ATTN_CU_MULTIPLE`` times the device's CU count and leaves every slice of an ``s_max``-long sequence at
+    least ``ATTN_MIN_SLICE`` keys. It looks at ``s_max``, not at the lengths, so it needs no device sync."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return max(1, min(ATTN_CU_MULTIPLE * cus // (b * hkv), s_max // ATTN_MIN_SLICE))
+
+
+def attn_decode_bf16(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, seq_lens: torch.Tensor,
+                     out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                     split_kv: int = 0, workspace: Optional[torch.Tensor] = None,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """out[b,h] = Σ_s softmax_s(scale · q[b,h]·k_cache[b,h//G,s]) · v_cache[b,h//G,s] over s < seq_lens[b].
+
+    ``q`` [B,Hq,128] and the contiguous caches [B,Hkv,S_max,128] are bfloat16, ``seq_lens`` [B] int32 with
+    1 ≤ len ≤ S_max, Hq = G·Hkv with 1 ≤ G ≤ 16 (any value); ``scale`` defaults to 128^-½. Accumulation is
+    fp32, the result [B,Hq,128] bfloat16. A cache must be smaller than 2^32 bytes.
+
+    Each sequence's keys are split over ``split_kv`` blocks (0: :func:`attn_split_kv`) whose fp32 partial
+    accumulators, maxima and sums go to ``workspace`` (float32, at least split_kv·B·Hq·130 elements, allocated
+    on the launch stream when absent) and are merged in ascending order by a second kernel, so the result is
+    bit-identical from run to run. ``q``, ``out`` and ``workspace`` must be 16-byte aligned.
+    """
+    if any(t.dtype != torch.bfloat16 for t in (q, k_cache, v_cache)):
+        raise TypeError("attn_decode_bf16 expects bfloat16 q, k_cache and v_cache")
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[0] != k_cache.shape[0]:
+        raise ValueError(f"shape mismatch: q{tuple(q.shape)} k_cache{tuple(k_cache.shape)} v_cache"
+                         f"{tuple(v_cache.shape)} (need q[B,Hq,128], caches [B,Hkv,S_max,128])")
+    b, hq, d = q.shape
+    hkv, s_max = k_cache.shape[1], k_cache.shape[2]
+    if d != 128 or k_cache.shape[3] != 128:
+        raise ValueError(f"attn_decode_bf16 needs head dim 128 (got {d} and {k_cache.shape[3]})")
+    if b == 0 or hkv == 0 or s_max == 0 or hq == 0 or hq % hkv:
+        raise ValueError(f"Hq must be a positive multiple of Hkv, B and S_max positive (got Hq {hq}, Hkv {hkv}, "
+                         f"B {b}, S_max {s_max})")
+    g = hq // hkv
+    if g > 16:
+        raise ValueError(f"attn_decode_bf16 needs Hq/Hkv <= 16 (got {g})")
+    if b * hkv * s_max * 256 >= 2 ** 32 or b > 65535:
+        raise ValueError("attn_decode_bf16 needs B <= 65535 and caches smaller than 2^32 bytes (B*Hkv*S_max*256)")
+    if seq_lens.dtype != torch.int32:
+        raise TypeError("seq_lens must be int32")
+    if seq_lens.shape != (b,) or not 0 <= split_kv <= 65535:
+        raise ValueError(f"seq_lens must be [{b}], got {tuple(seq_lens.shape)}; split_kv in 0..65535, got {split_kv}")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("k_cache and v_cache must be contiguous")
+    if not all(t.is_cuda and t.device == q.device for t in (q, k_cache, v_cache, seq_lens)):
+        raise ValueError("q, k_cache, v_cache and seq_lens must be on the same GPU")
+    q, seq_lens = q.contiguous(), seq_lens.contiguous()
+    if out is None:
+        out = torch.empty((b, hq, 128), dtype=torch.bfloat16, device=q.device)
+    elif out.shape != (b, hq, 128) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != q.device:
+        raise ValueError("out must be a contiguous bfloat16 [B,Hq,128] tensor on q's device")
+    split_kv = split_kv or attn_split_kv(b, hkv, s_max, q.device)
+    s = stream if stream is not None else torch.cuda.current_stream(q.device)
+    need = split_kv * b * hq * 130
+    if split_kv == 1:
+        workspace = None
+    elif workspace is None:
+        with torch.cuda.stream(s):
+            workspace = torch.empty(need, dtype=torch.float32, device=q.device)
+    elif (workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != q.device
+          or workspace.numel() < need):
+        raise ValueError(f"workspace must be a contiguous float32 tensor of at least split_kv*B*Hq*130 = {need} "
+                         f"elements on q's device")
+    native().attn_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), seq_lens.data_ptr(),
+                              out.data_ptr(), b, hkv, g, s_max, float(scale if scale is not None else 128 ** -0.5),
+                              split_kv, workspace.data_ptr() if workspace is not None else 0,
+                              workspace.numel() * 4 if workspace is not None else 0, int(s.cuda_stream))
+    return out
+
+
 #: The block-scaled precisions: (quantiser, GEMM) with one calling convention.
 _MX = {"mxfp8": (quantize_mxfp8, gemm_mxfp8_nt), "mxfp4": (quantize_mxfp4, gemm_mxfp4_nt)}
 
@@ -307,17 +388,26 @@ class Burner:
     ``batch`` (1..64, ``precision="mxfp4"`` only, ``size`` a multiple of 256) is
     the decode mix: the activation operand is ``[batch, size]`` and the GEMMs
     are :func:`gemm_mxfp4_skinny_nt`, which stream the weights from HBM.
+    ``context`` (with ``batch``, ``size`` a multiple of 1024) adds the other HBM
+    stream of a decode step: after each GEMM one :func:`attn_decode_bf16` of
+    ``size/128`` query heads in groups of 8 over a random bf16 KV cache of
+    ``context`` keys per sequence, its queries the GEMM's output.
     """
 
     def __init__(self, device: int = 0, size: int = 4096, gemms: int = 4, triad_mb: int = 1024,
-                 graph_iters: int = 0, precision: str = "bf16", batch: Optional[int] = None):
+                 graph_iters: int = 0, precision: str = "bf16", batch: Optional[int] = None,
+                 context: Optional[int] = None):
         if precision not in PRECISIONS:
             raise ValueError(f"unknown precision {precision!r}; one of {PRECISIONS}")
         if batch is not None and (precision != "mxfp4" or not 1 <= batch <= 64 or size % 256):
             raise ValueError(f"batch needs precision='mxfp4', 1 <= batch <= 64 and size%256==0 "
                              f"(got {precision!r}, batch {batch}, size {size})")
+        if context is not None and (batch is None or size % 1024 or context < 1):
+            raise ValueError(f"context needs batch, size%1024==0 and context >= 1 "
+                             f"(got batch {batch}, size {size}, context {context})")
         self.precision = precision
         self.batch = batch
+        self.context = context
         self.device = torch.device("cuda", device)
         self.size = size
         self.gemms = gemms
@@ -354,6 +444,21 @@ class Burner:
 
                         def gemm(aq, bq, as_, bs, out, stream):
                             gemm_mxfp4_skinny_nt(aq, bq, as_, bs, out=out, stream=stream, split_k=split, workspace=ws)
+
+                        if self.context:  # attention over the KV cache after every projection
+                            hq = self.size // 128
+                            kv = [torch.randn(self.batch, hq // 8, self.context, 128, device=self.device,
+                                              dtype=torch.bfloat16, generator=g) for _ in range(2)]
+                            lens = torch.full((self.batch,), self.context, device=self.device, dtype=torch.int32)
+                            o = torch.empty(self.batch, hq, 128, device=self.device, dtype=torch.bfloat16)
+                            asplit = attn_split_kv(self.batch, hq // 8, self.context, self.device)
+                            aws = torch.empty(asplit * self.batch * hq * 130, dtype=torch.float32, device=self.device)
+                            project = gemm
+
+                            def gemm(aq, bq, as_, bs, out, stream):
+                                project(aq, bq, as_, bs, out=out, stream=stream)
+                                attn_decode_bf16(out.view(self.batch, hq, 128), kv[0], kv[1], lens, out=o,
+                                                 stream=stream, split_kv=asplit, workspace=aws)
 
                 def one_iteration():
                     aq, as_ = quantise(a, stream=stream)
@@ -517,6 +622,55 @@ def time_gemm_skinny(m: int, n: int, k: int, iters: int = 20, device: int = 0, s
         times.append(s.elapsed_time(e) / 1e3 / count)
     times.sort()
     moved = n * k // 2 + n * k // 32 + m * k // 2 + m * k // 32 + m * n * 2
+    return moved / times[len(times) // 2] / 1e12
+
+
+def time_attn_decode(b: int, hkv: int, g: int, s: int, iters: int = 20, split_kv: int = 0, sdpa: bool = False,
+                     device: int = 0, lens=None) -> float:
+    """Median TB/s of attn_decode_bf16 over the bytes it must move: the K and V rows below each length, q and out.
+
+    Built like :func:`time_gemm_skinny`: the caches rotate over enough distinct K+V pairs to exceed 512 MiB when
+    one pair is smaller, a sample is one pass over all pairs between two events, enqueued behind a long triad,
+    divided by the number of pairs. ``lens`` (default: all ``s``) gives a ragged batch. ``sdpa=True`` times the
+    other route instead, over the same buffers and the same byte count:
+    ``torch.nn.functional.scaled_dot_product_attention`` on the same tensors with ``enable_gqa=True``, which
+    expands the KV heads to the query heads as that function requires, and, for a ragged batch, a boolean key mask.
+    """
+    dev = torch.device("cuda", device)
+    gen = torch.Generator(device=dev).manual_seed(b + hkv + g + s)
+    pair = 2 * b * hkv * s * 256
+    count = (512 << 20) // pair + 1 if pair < (512 << 20) else 1
+    caches = [[torch.randn(b, hkv, s, 128, device=dev, dtype=torch.bfloat16, generator=gen) for _ in range(2)]
+              for _ in range(count)]
+    q = torch.randn(b, hkv * g, 128, device=dev, dtype=torch.bfloat16, generator=gen)
+    out = torch.empty_like(q)
+    lens_list = [s] * b if lens is None else list(lens)
+    seq_lens = torch.tensor(lens_list, device=dev, dtype=torch.int32)
+    split = split_kv or attn_split_kv(b, hkv, s, dev)
+    ws = torch.empty(split * b * hkv * g * 130, device=dev, dtype=torch.float32) if split > 1 else None
+    mask = None if lens is None else (torch.arange(s, device=dev)[None, :] < seq_lens[:, None])[:, None, None, :]
+    x, y, z = (torch.rand(1 << 28, device=dev) for _ in range(3))
+
+    def one_pass():
+        for k, v in caches:
+            if sdpa:
+                torch.nn.functional.scaled_dot_product_attention(q[:, :, None], k, v, attn_mask=mask, enable_gqa=True)
+            else:
+                attn_decode_bf16(q, k, v, seq_lens, out=out, split_kv=split, workspace=ws)
+
+    one_pass()
+    torch.cuda.synchronize(dev)
+    times = []
+    for _ in range(iters):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        stream_triad(x, y, 0.5, out=z)  # ~0.6 ms: the pass below is enqueued before the device reaches it
+        t0.record()
+        one_pass()
+        t1.record()
+        t1.synchronize()
+        times.append(t0.elapsed_time(t1) / 1e3 / count)
+    times.sort()
+    moved = 2 * hkv * 256 * sum(lens_list) + 2 * b * hkv * g * 256
     return moved / times[len(times) // 2] / 1e12
 
 
