@@ -483,6 +483,8 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* _
 #include "gemm_mxfp4_skinny.h"
 // Decode attention over a bf16 KV cache: attn_decode, its split-KV combine, launcher and Python binding.
 #include "attn_decode.h"
+// Prefill attention over the same cache: attn_prefill (causal, K and V shared through LDS), launcher and Python binding.
+#include "attn_prefill.h"
 
 // One pass, no grid-stride loop: each thread moves TRIAD_U 16-byte vectors,
 // all loads issued before any store (memory-level parallelism), and the
@@ -674,6 +676,7 @@ PyMethodDef kMethods[] = {
      "mandatory E8M0 scales per 32 along K; K a multiple of 512."},
     {"gemm_mxfp4_skinny_nt", py_gemm_mxfp4_skinny, METH_VARARGS, kSkinnyDoc},
     {"attn_decode_bf16", py_attn_decode, METH_VARARGS, kAttnDecodeDoc},
+    {"attn_prefill_bf16", py_attn_prefill, METH_VARARGS, kAttnPrefillDoc},
     {"quantize_mxfp4", py_quantize_mxfp4, METH_VARARGS,
      "quantize_mxfp4(x, q, scales, rows, K, stream): bf16 [rows,K] -> packed e2m1 [rows,K/2] + E8M0 [rows,K/32]."},
     {"stream_triad", py_triad, METH_VARARGS, "stream_triad(a, b, c, n, s, stream): c = a + s*b (fp32)."},

@@ -13,6 +13,7 @@
 * :func:`attn_decode_bf16` — decode attention ``softmax(q·Kᵀ)·V`` of one new token per
   sequence over a bf16 KV cache with grouped query heads: the cache streamed once from
   HBM, the keys split over blocks, partials merged in a fixed order
+* ``attn_prefill_bf16`` — causal prefill attention over the same cache, lives in :mod:`.attention` (ops/attention.py)
 * :class:`Burner` — runs a GEMM + triad mix on a side stream for a target
   duration: the synthetic "GPU pod" whose power / HBM / activity the
   exporter reports (``precision="mxfp8"`` / ``"mxfp4"``: inference-like mixes;
