@@ -485,6 +485,8 @@ __global__ __launch_bounds__(P8_THREADS) void gemm_bf16_nt_8ph(const uint16_t* _
 #include "attn_decode.h"
 // Prefill attention over the same cache: attn_prefill (causal, K and V shared through LDS), launcher and Python binding.
 #include "attn_prefill.h"
+// FP8 KV cache: kv_append_fp8 (fills it) and attn_decode_fp8 (decode attention over it), launchers and Python bindings.
+#include "attn_decode_fp8.h"
 
 // One pass, no grid-stride loop: each thread moves TRIAD_U 16-byte vectors,
 // all loads issued before any store (memory-level parallelism), and the
@@ -677,6 +679,8 @@ PyMethodDef kMethods[] = {
     {"gemm_mxfp4_skinny_nt", py_gemm_mxfp4_skinny, METH_VARARGS, kSkinnyDoc},
     {"attn_decode_bf16", py_attn_decode, METH_VARARGS, kAttnDecodeDoc},
     {"attn_prefill_bf16", py_attn_prefill, METH_VARARGS, kAttnPrefillDoc},
+    {"attn_decode_fp8", py_attn_decode_fp8, METH_VARARGS, kAttnDecodeFp8Doc},
+    {"kv_append_fp8", py_kv_append_fp8, METH_VARARGS, kKvAppendFp8Doc},
     {"quantize_mxfp4", py_quantize_mxfp4, METH_VARARGS,
      "quantize_mxfp4(x, q, scales, rows, K, stream): bf16 [rows,K] -> packed e2m1 [rows,K/2] + E8M0 [rows,K/32]."},
     {"stream_triad", py_triad, METH_VARARGS, "stream_triad(a, b, c, n, s, stream): c = a + s*b (fp32)."},
